@@ -790,6 +790,27 @@ def scaling_projection(model, dev, whole_ms, steps=3):
     return out
 
 
+DUMP_SEG_PIXELS = 131072           # segmentation pixels --dump-outputs keeps of a whole frame (26 MB of 50 classes)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, image, segmentation, rank=None):
+    """--dump-outputs: the last timed step's results as float32 .npy files — `image` whole ([1, rows, W, 3], 7.7 MB
+    for the frame) and `segmentation` ([1, rows, W, 50], 128 MB for the frame) as the rows of a fixed, seeded sample
+    of its pixels (`segmentation_sample`, [n, 50], pixel indices sorted; n in proportion to the rows rendered).  The
+    inputs (seed-0 weights, fixed pose, deterministic fenceposts) are the same from run to run, so two builds can be
+    compared file by file.  With several ranks every rank writes its own row block, names suffixed _rank<r>."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank is None else f"_rank{rank}"
+    pixels = segmentation.shape[0] * segmentation.shape[1] * segmentation.shape[2]
+    n = min(pixels, max(1, DUMP_SEG_PIXELS * pixels // (IMAGE * IMAGE)))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, size=n, replace=False))
+    seg = segmentation.reshape(pixels, segmentation.shape[-1])[torch.from_numpy(pick).to(segmentation.device)]
+    for name, t in (("image", image), ("segmentation_sample", seg)):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -804,9 +825,14 @@ def main():
     ap.add_argument("--precision", choices=("fp32", "f16x3"), default=os.environ.get("NERF_BENCH_PRECISION", "fp32"))
     ap.add_argument("--dry-run", action="store_true",
                     help="launch, rendezvous (gloo) and partitions only: no GPU call, nothing measured")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32): the image, and a fixed seeded sample of the segmentation's pixels")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: become it (before any GPU call; a child process, never an exec)
@@ -871,8 +897,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def measure(scaling, steps, warmup):
-        """W untimed + K timed steps between barrier + synchronize pairs; MAX over ranks."""
+    def measure(scaling, steps, warmup, keep_outputs=False):
+        """W untimed + K timed steps between barrier + synchronize pairs; MAX over ranks.  `keep_outputs`: the
+        (image, segmentation) of the last timed step go into the result as "outputs"."""
         pose, rows = workload(scaling)
         cam_o, cam_r = look_at(pose)
         cam_o, cam_r = cam_o.to(dev), cam_r.to(dev)
@@ -901,9 +928,12 @@ def main():
         rays_rank = (rows[1] - rows[0]) * IMAGE
         total_rays = rays_rank * world if scaling == "weak" else IMAGE * IMAGE
         return {"elapsed": float(t.item()), "kernel_ms": kernel_ms, "launches": launches,
-                "rays_per_rank": rays_rank, "value": total_rays * SAMPLES * steps / float(t.item())}
+                "rays_per_rank": rays_rank, "value": total_rays * SAMPLES * steps / float(t.item()),
+                **({"outputs": out} if keep_outputs else {})}
 
-    m = measure(args.scaling, args.steps, args.warmup)
+    m = measure(args.scaling, args.steps, args.warmup, keep_outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, *m.pop("outputs"), rank=rank if world > 1 else None)
     weak = dp = None
     if distributed and args.scaling == "strong":
         weak = measure("weak", args.steps, args.warmup)

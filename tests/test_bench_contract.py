@@ -117,3 +117,38 @@ def test_launcher_and_gpus_disagreeing_is_a_message_not_an_assert():
     assert run.returncode == 2 and "WORLD_SIZE=2" in run.stderr and "AssertionError" not in run.stderr
     one = _bench("--gpus", "1", "--dry-run")                     # N = 1: no launcher, no rendezvous
     assert one.returncode == 0 and json.loads(one.stdout.strip().splitlines()[-1])["config"]["rays_per_gpu"] == 640000
+
+
+def test_dump_outputs_writes_float32_arrays_within_64_mb(tmp_path):
+    """--dump-outputs: the whole image and a fixed seeded pixel sample of the segmentation, float32, <= 64 MB for the
+    full 800x800 frame; the sample is the same from call to call (two builds compare file by file); N > 1 ranks
+    write their own row blocks under suffixed names."""
+    import numpy as np
+    import torch
+    import bench
+    image = torch.rand(1, bench.IMAGE, bench.IMAGE, 3)
+    pixels = torch.arange(bench.IMAGE * bench.IMAGE, dtype=torch.float32)        # every class holds its pixel's index
+    seg = pixels.reshape(1, bench.IMAGE, bench.IMAGE, 1).repeat(1, 1, 1, 50)
+    for out in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(out), image, seg)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["image.npy", "segmentation_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "image.npy"), image.numpy())
+    sample = np.load(tmp_path / "a" / "segmentation_sample.npy")
+    assert sample.shape == (bench.DUMP_SEG_PIXELS, 50)
+    pixel = sample[:, 0].astype(np.int64)              # the sample's rows are whole pixels, in increasing order
+    assert np.array_equal(sample, seg.reshape(-1, 50).numpy()[pixel]) and (np.diff(pixel) > 0).all()
+    bench.dump_outputs(str(tmp_path / "r"), image[:, :100], seg[:, :100], rank=3)
+    assert sorted(os.listdir(tmp_path / "r")) == ["image_rank3.npy", "segmentation_sample_rank3.npy"]
+    assert np.load(tmp_path / "r" / "segmentation_sample_rank3.npy").shape == (bench.DUMP_SEG_PIXELS // 8, 50)
+
+
+def test_steps_and_dump_outputs_are_options():
+    run = _bench("--gpus", "1", "--steps", "0", "--dry-run")
+    assert run.returncode == 2 and "--steps must be at least 1" in run.stderr
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--dump-outputs"' in src and '"ms_per_step": m["elapsed"] / args.steps * 1e3' in src

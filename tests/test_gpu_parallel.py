@@ -4,6 +4,7 @@ driver's scaling bench).  Checks with the real HIP kernels: row-sharded render =
 all-reduced data-parallel gradients == single-process gradients of the concatenated batch for an
 UNEVEN split (weighted by local / global rays, reduced in place on the backward's flat vector), and
 the in-kernel draws of the two ranks differ."""
+import gc
 import os
 
 import pytest
@@ -292,6 +293,11 @@ def _rccl_single_rank_worker(rank, world, port, out_dir):
         moved = any(not torch.equal(a, b) for a, b in zip(before, run.model.parameters()))
         torch.save(dict(dp=dp, losses=losses, counter=counter, moved=moved, captured=run._graph is not None),
                    os.path.join(out_dir, "rccl1.pt"))
+        # the trainer's step graph holds a captured RCCL collective: release it and let the device drain BEFORE the
+        # communicator is finalised (destroy_process_group), not while it is being torn down
+        del run
+        gc.collect()
+        torch.cuda.synchronize(dev)
     finally:
         dist.destroy_process_group()
 

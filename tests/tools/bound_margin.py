@@ -2,8 +2,9 @@
 gradient in both training arithmetics, with the factors of the split-precision scale BOUND pushed to where it is loosest
 (tests/test_gpu_backward.py: test_layer0_weight_gradient_under_a_loose_scale_bound asserts the same configurations).
 usage: python tests/tools/bound_margin.py"""
-import sys, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, torch
+TESTS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(TESTS)); sys.path.insert(0, TESTS)
 import test_gpu_backward as T
 dev = torch.device("cuda:0")
 O, CFG = T.O, T.CFG
