@@ -170,7 +170,8 @@ size_t nerf_hip_grad_elements(int32_t hidden, int32_t enc_inputs, int32_t num_ou
 /* Backward of nerf_hip_render_forward w.r.t. the parameters (replaces PyTorch autograd through
  * NeRF.render_rays, driven by loss.backward() at train_conditional_nerf.py:133).  `fwd` must be
  * the argument block of the training forward call (same rays, sampling inputs, draws, packed
- * image and train_workspace, which that call filled); rays are not differentiated.
+ * image and train_workspace, which that call filled).  Rays are not differentiated here:
+ * nerf_hip_render_backward_rays below is the same call that also writes dL/d rays_o and dL/d rays_d.
  * Two forms: the loss reached the COMPOSITED outputs (d_rgb, optionally d_seg; d_raw NULL: NeRF.render_rays,
  * model.py:596-668), or it reached the PER-SAMPLE network outputs of NeRF.forward (model.py:553-594: density |
  * color | segmentation logits; d_raw non-NULL, d_rgb / d_seg ignored) — then the compositing backward is skipped
@@ -186,6 +187,27 @@ typedef struct NerfHipBackwardArgs {
 
 size_t nerf_hip_backward_scratch_bytes(int64_t n_rays, int32_t num_samples);
 int nerf_hip_render_backward(const NerfHipBackwardArgs* args, void* stream);
+
+/* Backward of nerf_hip_render_forward w.r.t. the RAYS as well (pose refinement; the reference's autograd reaches
+ * rays_o / rays_d through NeRF.render_rays and NeRF.forward, nerf/model.py:544-594, :596-668).  Launches, in order:
+ * the compositing backward (or the d_raw scatter), the data gradient, the weight gradient and its reduce (only if
+ * bwd.grad is non-NULL: then `grad` is bit-identical to nerf_hip_render_backward on the same inputs), and the ray
+ * gradient.  The ray gradient takes both routes of a sample: through the network input (dL/dh = dY_0 W_0 back
+ * through the integrated positional encoding and the conical frustum) and, for the composited form (d_raw NULL),
+ * through the distances between consecutive means; with d_mean also the means NeRF.forward returns.  The fenceposts
+ * are constants (recomputed exactly as the forward drew them: table, u, t_values or Philox — for the last, rng_counter
+ * must hold the value the forward read).  Rays must be explicit arrays (fwd.rays_o / rays_d), not cameras. */
+typedef struct NerfHipRayBackwardArgs {
+    NerfHipBackwardArgs bwd;    /* exactly as for nerf_hip_render_backward; bwd.grad NULL = parameters frozen     */
+    const float* w0;            /* [hidden, enc_inputs] prediction_heads.0.weight (PyTorch layout) of the forward */
+    const float* d_mean;        /* [n_rays,S-1,3] dL/d mean (NeRF.forward), or NULL                               */
+    float* d_rays_o;            /* [n_rays,3] written (not accumulated), or NULL                                  */
+    float* d_rays_d;            /* [n_rays,3] written (not accumulated), or NULL                                  */
+    float* ray_scratch;         /* nerf_hip_ray_backward_scratch_bytes() bytes                                    */
+} NerfHipRayBackwardArgs;
+
+size_t nerf_hip_ray_backward_scratch_bytes(int64_t n_rays, int32_t num_samples);
+int nerf_hip_render_backward_rays(const NerfHipRayBackwardArgs* args, void* stream);
 
 /* Batched replacement of PixelRayDataset.__getitem__ + default_collate (nerf/dataset.py:246-316,
  * train_conditional_nerf.py:100-101): decode flat example ids (w = id % W, h = (id / W) % H,
@@ -343,7 +365,8 @@ int nerf_hip_mse_loss(const NerfHipMseArgs* args, void* stream);
 #define NERF_HIP_TIMING_ADAM 6
 #define NERF_HIP_TIMING_LOSS 7
 #define NERF_HIP_TIMING_PACK 8                /* parameter re-layout (either network)                            */
-#define NERF_HIP_TIMING_TAGS 9
+#define NERF_HIP_TIMING_RAY_GRADIENT 9        /* dL/d rays of nerf_hip_render_backward_rays                       */
+#define NERF_HIP_TIMING_TAGS 10
 int nerf_hip_timing(int enable);
 int nerf_hip_timing_read(int reset, double* avg_ms, int64_t* launches);
 int nerf_hip_timing_read_tagged(int reset, int32_t n_tags, double* avg_ms, int64_t* launches);

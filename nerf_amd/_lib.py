@@ -47,6 +47,12 @@ class BackwardArgs(ctypes.Structure):
                 ("scratch", _f32p), ("d_raw", _f32p)]
 
 
+class RayBackwardArgs(ctypes.Structure):
+    """Mirror of NerfHipRayBackwardArgs (include/nerf_hip.h)."""
+    _fields_ = [("bwd", BackwardArgs), ("w0", _f32p), ("d_mean", _f32p), ("d_rays_o", _f32p), ("d_rays_d", _f32p),
+                ("ray_scratch", _f32p)]
+
+
 class GatherArgs(ctypes.Structure):
     """Mirror of NerfHipGatherArgs (include/nerf_hip.h)."""
     _fields_ = [("index", _f32p), ("n", ctypes.c_int64), ("images", _f32p), ("segmentation", _f32p),
@@ -145,6 +151,10 @@ def lib():
     handle.nerf_hip_backward_scratch_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]
     handle.nerf_hip_render_backward.restype = ctypes.c_int
     handle.nerf_hip_render_backward.argtypes = [ctypes.POINTER(BackwardArgs), ctypes.c_void_p]
+    handle.nerf_hip_ray_backward_scratch_bytes.restype = ctypes.c_size_t
+    handle.nerf_hip_ray_backward_scratch_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]
+    handle.nerf_hip_render_backward_rays.restype = ctypes.c_int
+    handle.nerf_hip_render_backward_rays.argtypes = [ctypes.POINTER(RayBackwardArgs), ctypes.c_void_p]
     handle.nerf_hip_gather_pixel_rays.restype = ctypes.c_int
     handle.nerf_hip_gather_pixel_rays.argtypes = [ctypes.POINTER(GatherArgs), ctypes.c_void_p]
     handle.nerf_hip_resample_pdf.restype = ctypes.c_int
@@ -195,7 +205,7 @@ def lib():
 EXPORTS = ("nerf_hip_version", "nerf_hip_last_error", "nerf_hip_build_flags", "nerf_hip_packed_bytes",
            "nerf_hip_pack_weights", "nerf_hip_render_forward", "nerf_hip_train_workspace_bytes",
            "nerf_hip_grad_elements", "nerf_hip_backward_scratch_bytes", "nerf_hip_render_backward",
-           "nerf_hip_gather_pixel_rays", "nerf_hip_resample_pdf", "nerf_hip_legacy_packed_bytes",
+           "nerf_hip_ray_backward_scratch_bytes", "nerf_hip_render_backward_rays", "nerf_hip_gather_pixel_rays", "nerf_hip_resample_pdf", "nerf_hip_legacy_packed_bytes",
            "nerf_hip_legacy_pack_weights", "nerf_hip_legacy_render_forward",
            "nerf_hip_legacy_train_workspace_bytes", "nerf_hip_legacy_grad_elements",
            "nerf_hip_legacy_backward_scratch_bytes", "nerf_hip_legacy_render_backward", "nerf_hip_adam_step", "nerf_hip_mse_loss",
@@ -232,13 +242,13 @@ def timing_read(reset=True):
     return avg.value, n.value
 
 
-TIMING_TAGS = 9         # NERF_HIP_TIMING_TAGS
+TIMING_TAGS = 10        # NERF_HIP_TIMING_TAGS
 
 
 def timing_read_tagged(reset=True):
     """{tag name: (average ms, launches)} of every launch kind recorded since the last reset (the launches of a
     training step: forward, composite_forward, composite_backward, data_gradient, weight_gradient, reduce, adam,
-    loss, pack); tags without a launch are left out."""
+    loss, pack, and ray_gradient of a backward that differentiates the rays); tags without a launch are left out."""
     avg = (ctypes.c_double * TIMING_TAGS)()
     n = (ctypes.c_int64 * TIMING_TAGS)()
     check(lib().nerf_hip_timing_read_tagged(1 if reset else 0, TIMING_TAGS, avg, n), "nerf_hip_timing_read_tagged")

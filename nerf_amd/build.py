@@ -45,7 +45,7 @@ CODEGEN_FLAGS = ["-O3", "-std=c++17"]
 # nerf_sampler.hip (gather / resampler / Adam: no MFMAs of their own, but they may share a SIMD with another
 # stream's): SLP gains nothing there and did produce the op_sel form in the Adam kernel's powf.
 FILE_FLAGS = {"nerf_render.hip": ["-fno-slp-vectorize"], "nerf_legacy.hip": ["-fno-slp-vectorize"],
-              "nerf_sampler.hip": ["-fno-slp-vectorize"]}
+              "nerf_sampler.hip": ["-fno-slp-vectorize"], "nerf_ray_backward.hip": ["-fno-slp-vectorize"]}
 
 
 def flags_for(path):

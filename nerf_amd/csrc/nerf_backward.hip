@@ -780,21 +780,17 @@ int choose_splits(int64_t n_tiles) {
 
 }  // namespace
 
-extern "C" {
-
-size_t nerf_hip_backward_scratch_bytes(int64_t n_rays, int32_t num_samples) {
-    if (n_rays <= 0 || num_samples < 2) return 0;
-    return ((size_t)kMaxSplits * kSlabFloats + (size_t)kMaxDataGrid * (kGbFloats + 8)) * sizeof(float);
-}
-
-int nerf_hip_render_backward(const NerfHipBackwardArgs* args, void* stream) {
+// The launches of nerf_hip_render_backward; `weights` = false (nerf_hip_render_backward_rays with frozen parameters)
+// stops after the data gradient: no weight gradient, no reduce, `grad` may be NULL.
+int nerf_bwd::render_backward_launches(const NerfHipBackwardArgs* args, void* stream, bool weights) {
     if (args == nullptr) return nerf_common::fail(NERF_HIP_EINVAL, "render_backward: null args");
     const NerfHipRenderArgs& a = args->fwd;
-    if (args->grad == nullptr)
+    if (weights && args->grad == nullptr)
         return nerf_common::fail(NERF_HIP_EINVAL, "render_backward: grad is null");
     if (!shape_ok(shape_of(a)))
         return nerf_common::fail(NERF_HIP_EUNSUPPORTED, "render_backward: network shape out of range (hidden 1 .. 256, enc_inputs "
                                                         "6 .. 96 in steps of 6, color_outputs 1 .. 12, num_outputs 1 + color_outputs .. 64)");
+    if (a.n_rays == 0 && !weights) return 0;
     if (a.n_rays == 0)      // empty batch (an empty data-parallel shard): the gradient is zero
         return nerf_common::check_hip(hipMemsetAsync(args->grad, 0, (size_t)grad_elements(shape_of(a)) * sizeof(float),
                                                      (hipStream_t)stream), "render_backward memset");
@@ -887,6 +883,7 @@ int nerf_hip_render_backward(const NerfHipBackwardArgs* args, void* stream) {
         else if (tt == 8) hipLaunchKernelGGL(nerf_bwd_data_n_kernel<8>, dim3((unsigned)grid), dim3(256), kBwdLdsBytes, st, ba);
         else hipLaunchKernelGGL(nerf_bwd_data_kernel, dim3((unsigned)grid), dim3(256), kBwdLdsBytes, st, ba);
     }
+    if (!weights) return nerf_common::check_hip(hipGetLastError(), "render_backward launch");
     const int wgrad_jobs = 6;
     const bool wgrad_half = half;
     {
@@ -908,6 +905,17 @@ int nerf_hip_render_backward(const NerfHipBackwardArgs* args, void* stream) {
                            0, st, ba);
     }
     return nerf_common::check_hip(hipGetLastError(), "render_backward launch");
+}
+
+extern "C" {
+
+size_t nerf_hip_backward_scratch_bytes(int64_t n_rays, int32_t num_samples) {
+    if (n_rays <= 0 || num_samples < 2) return 0;
+    return ((size_t)kMaxSplits * kSlabFloats + (size_t)kMaxDataGrid * (kGbFloats + 8)) * sizeof(float);
+}
+
+int nerf_hip_render_backward(const NerfHipBackwardArgs* args, void* stream) {
+    return nerf_bwd::render_backward_launches(args, stream, true);
 }
 
 }  // extern "C"

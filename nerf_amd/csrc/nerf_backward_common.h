@@ -1014,5 +1014,9 @@ __device__ __forceinline__ float wave_strided_sum(const float* p, int n, int64_t
     return sum;
 }
 
+// nerf_backward.hip: the launches of nerf_hip_render_backward (compositing backward or d_raw scatter, data gradient,
+// then — `weights` — weight gradient and reduce into args->grad); nerf_hip_render_backward_rays runs them first.
+int render_backward_launches(const NerfHipBackwardArgs* args, void* stream, bool weights);
+
 }  // namespace nerf_bwd
 #endif

@@ -1166,7 +1166,7 @@ int nerf_hip_timing_read_tagged(int reset, int32_t n_tags, double* avg_ms, int64
 const char* nerf_hip_timing_tag_name(int32_t tag) {
     static const char* const names[NERF_HIP_TIMING_TAGS] = {
         "forward", "composite_forward", "composite_backward", "data_gradient", "weight_gradient",
-        "reduce", "adam", "loss", "pack"};
+        "reduce", "adam", "loss", "pack", "ray_gradient"};
     return tag >= 0 && tag < NERF_HIP_TIMING_TAGS ? names[tag] : nullptr;
 }
 

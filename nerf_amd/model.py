@@ -490,18 +490,20 @@ class NeRF(nn.Module):
         network: nerf_amd/backward.py FieldFunction); under ``torch.no_grad()`` it is the plain inference launch.
         Arithmetic: the differentiable call is a TRAINING forward and runs in ``self.train_precision`` (its backward
         must match it), the no_grad call in ``self.precision``; with the two set differently the same inputs give
-        values that differ by the arithmetics' distance (~1e-6).  NOT differentiable w.r.t. ``rays_o`` /
-        ``rays_d`` / ``samples`` (the reference's autograd reaches them; its scripts never ask): they are detached,
-        with a warning when one of them requires grad."""
+        values that differ by the arithmetics' distance (~1e-6).  Differentiable w.r.t. ``rays_o`` / ``rays_d`` too
+        (through ``mean`` and the network outputs, as the reference's autograd is: a pose can be fitted with the
+        network frozen).  NOT differentiable w.r.t. ``samples`` (the reference's autograd reaches them; its scripts
+        never ask): they are detached, with a warning when they require grad."""
         _require_device(rays_o, "rays_o"), _require_device(rays_d, "rays_d")
         _require_device(samples, "samples")
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (rays_o, rays_d, samples)):
+        if torch.is_grad_enabled() and samples.requires_grad:
             import warnings
-            warnings.warn("nerf_amd.NeRF.forward is differentiable w.r.t. the parameters only: rays_o / rays_d / "
-                          "samples are detached (no gradient reaches them)", stacklevel=2)
+            warnings.warn("nerf_amd.NeRF.forward is not differentiable w.r.t. samples: they are detached (no "
+                          "gradient reaches them)", stacklevel=2)
         n_rays, num_samples = samples.shape[0], samples.shape[-1]
-        o, d, t = rays_o.detach().contiguous(), rays_d.detach().contiguous(), samples.detach().contiguous()
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        o, d, t = rays_o.contiguous(), rays_d.contiguous(), samples.detach().contiguous()
+        if torch.is_grad_enabled() and (o.requires_grad or d.requires_grad or
+                                        any(p.requires_grad for p in self.parameters())):
             from .backward import FieldFunction
             mean, raw = FieldFunction.apply(self, o, d, t, *self._param_list())
         else:
@@ -547,8 +549,8 @@ class NeRF(nn.Module):
         (bit-reproducible stochastic path); otherwise they are drawn per ``self.rng``."""
         _require_device(rays_o, "rays_o"), _require_device(rays_d, "rays_d")
         lead = rays_o.shape[:-1]
-        flat_o = rays_o.detach().reshape(-1, 3).contiguous()
-        flat_d = rays_d.detach().reshape(-1, 3).contiguous()
+        flat_o = rays_o.reshape(-1, 3).contiguous()          # (rays that require grad stay in the graph)
+        flat_d = rays_d.reshape(-1, 3).contiguous()
         n_rays = flat_o.shape[0]
         mode = 0
         if u is None and noise is None:
@@ -659,13 +661,16 @@ class NeRF(nn.Module):
         (the reference has no ``no_grad`` inside, model.py:754-770; its callers wrap the call,
         train_conditional_nerf.py:139): the frame then goes through ``render_rays`` chunk by chunk exactly as
         the reference's loop does, every chunk keeping its training workspace (11 KB per sample) until the
-        backward.  Wrap inference in ``torch.no_grad()`` for the one-launch path."""
+        backward.  The same holds when ``camera_o`` or ``camera_r`` requires grad: the rays are then built by the
+        torch ``rays_to_world_coordinates``, so the pose receives the ray gradient.  Wrap inference in
+        ``torch.no_grad()`` for the one-launch path."""
         _require_device(camera_o, "camera_o"), _require_device(camera_r, "camera_r")
         device = camera_o.device
         batch = camera_o.shape[0]
         row_end = image_h if row_end is None else row_end
         rows = row_end - row_begin
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if torch.is_grad_enabled() and (camera_o.requires_grad or camera_r.requires_grad or
+                                        any(p.requires_grad for p in self.parameters())):
             # the reference's body (model.py:727-770) on the differentiable render_rays
             rays = self.generate_rays(image_h, image_w, focal_length, dtype=camera_o.dtype, device=device)
             rays = torch.broadcast_to(rays[row_begin:row_end].unsqueeze(0), [batch, rows, image_w, 3])
